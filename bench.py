@@ -11,8 +11,14 @@ the cross-shard transport (tgsim_comm_init: an RCCL communicator over xGMI): eve
 single-shard calls, the window's exchange (the peer blocks, whole - no host read of their counts) and
 the storm batch's MAX all-reduce run inside them on the simulator's stream.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
+
+A plain run sets up, warms up, times the K steps and prints the line: metric, value, ms_per_step and
+the configuration. --full adds what takes runs or passes of its own: the per-kernel probe and the
+HIP events around the dominant kernel (roofline, kernels_probe), the CPU oracle (cpu_baseline) and,
+for the storm, config 5 beside the headline. --dump-outputs DIR writes what the last timed step
+computed (statuses, deliveries, inbox offsets) as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -179,11 +185,16 @@ def roofline(dominant: str, delta: dict, kern_ms: float, kern_n: int, n_local: i
     }
 
 
+SETTLE_STEPS = 10
+
+
 def probe_steps(args) -> int:
-    """Probe steps before the timed region: as many as it has (at least 10), so the dominant kernel
-    is chosen over as many launches as the timed region makes (a 5-step probe flipped
-    between two kernels within 2 %)."""
-    return max(10, args.steps)
+    """Untimed steps between the warm-up and the timed region. --full: the kernel probe, as many
+    steps as the timed region has (at least 10), so the dominant kernel is chosen over as many
+    launches as the timed region makes (a 5-step probe flipped between two kernels
+    within 2 %). A plain run: 10 unprofiled steps in the probe's place, so the timed steps start
+    at least 10 steps past --warmup as they always have (up to 10 timed steps: the very same ones)."""
+    return max(SETTLE_STEPS, args.steps) if args.full else SETTLE_STEPS
 
 
 def probe_kernels(sim, step, first: int, probe: int):
@@ -201,6 +212,43 @@ def probe_kernels(sim, step, first: int, probe: int):
     # 8(d) assigns it bytes (its roofline then says so with frac 0)
     ranked = sorted(((v["total_ms"], k) for k, v in ks.items() if k not in COLLECTIVES), reverse=True)
     return ks, (ranked[0][1] if ranked else "k_emit_bucket")
+
+
+def settle_or_probe(args, sim, step, collectives: bool = False):
+    """The steps between the warm-up and the timed region (probe_steps). --full: the kernel probe,
+    then HIP events around the dominant kernel (and the collectives) only, for the timed region;
+    returns (kernels_probe, dominant, the profile's base). A plain run: the same steps, unprofiled;
+    returns (None, None, None)."""
+    probe = probe_steps(args)
+    if not args.full:
+        for r in range(args.warmup, args.warmup + probe):
+            step(r)
+        return None, None, None
+    kernels, dominant = probe_kernels(sim, step, args.warmup, probe)
+    sim.profile([dominant] + (list(COLLECTIVES) if collectives else []))
+    return kernels, dominant, sim.profile_read()
+
+
+OUTPUT_BYTES = 60 << 20  # --dump-outputs: all arrays of a run together (float64), under 64 MB
+
+
+def dump_outputs(sim, out_dir: str, rank: int = 0, world: int = 1) -> None:
+    """--dump-outputs: what a caller receives after the last timed step - every input message's
+    status, the window's deliveries (one array per field), the inbox offsets and the clock - as
+    <out_dir>/<name>.npy (float64: every field is an integer below 2^53; a shard of a sharded run
+    writes <name>_rank<r>.npy). Where the arrays together exceed OUTPUT_BYTES, one over its equal
+    share is written as a fixed sample: the elements at the sorted indices default_rng(0) draws for
+    its length."""
+    arrays = {"status": sim.status(), "inbox_offsets": sim.inbox_offsets(),
+              "now": np.array([sim.now], np.int64)}
+    arrays.update({f"deliv_{k}": v for k, v in sim.deliveries().items()})
+    os.makedirs(out_dir, exist_ok=True)
+    whole = 8 * sum(len(a) for a in arrays.values()) <= OUTPUT_BYTES
+    cap = OUTPUT_BYTES // 8 // len(arrays)
+    for name, a in arrays.items():
+        if not whole and len(a) > cap:
+            a = a[np.sort(np.random.default_rng(0).choice(len(a), cap, replace=False))]
+        np.save(os.path.join(out_dir, name + (f"_rank{rank}" if world > 1 else "") + ".npy"), a.astype(np.float64))
 
 
 def counters(sim) -> dict:
@@ -268,7 +316,13 @@ def parse():
     p.add_argument("--seed", type=int, default=4)
     p.add_argument("--max-records", type=int, default=1 << 23)
     p.add_argument("--cpu-seconds", type=float, default=15.0)
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle")
+    p.add_argument("--full", action="store_true",
+                   help="also the per-kernel probe and roofline, the CPU oracle baseline and (storm) config 5 "
+                        "beside the headline; a plain run times the steps and prints metric, value, ms_per_step")
+    p.add_argument("--dump-outputs", metavar="DIR",
+                   help="write what the last timed step computed (statuses, deliveries, inbox offsets) as "
+                        "DIR/<name>.npy")
     # config 5 (not the headline): 1M-instance random-regular pubsub flood, one window per step
     p.add_argument("--workload", choices=("storm", "flood", "a2a", "splitbrain"), default="storm")
     p.add_argument("--a2a-instances", type=int, default=1000)
@@ -289,7 +343,7 @@ def parse():
                    help="flood: max_records per publication of a wave (the wheel arena is twice it; "
                         "heavier waves need more than the default's headroom: tools/flood_load.sh)")
     p.add_argument("--no-beside", action="store_true",
-                   help="storm: skip config 5 (the 1M flood, same GPU count) reported beside the headline")
+                   help="storm with --full: skip config 5 (the 1M flood, same GPU count) reported beside the headline")
     a = p.parse_args()
     if a.workload == "splitbrain":
         a.warmup = a.warmup if "--warmup" in sys.argv else 200
@@ -317,7 +371,9 @@ def exchange_cap(per_window: int, n_shards: int) -> int:
     return int(1.25 * per_window / (s * s)) + 4096
 
 
-def sim_config(args, shard=0, n_shards=1, device=0):
+def sim_config(args, shard=0, n_shards=1, device=0, rounds=0):
+    """rounds: the storm rounds the context will run; every round's barrier is a sync state of its
+    own (state id = round), so a run longer than the default 4096 states gets that many."""
     from testground_amd.sim import SimConfig
     # TCP with ACKs: a window stages the round's writes plus the last window's ACKs (one per
     # delivered data packet) plus the fired timers, and keeps about twice the records in flight
@@ -325,7 +381,8 @@ def sim_config(args, shard=0, n_shards=1, device=0):
     per_window = args.instances * args.fanout * (2 if acks else 1) + (1 << 16 if acks else 0)
     return SimConfig(n_instances=args.instances, seed=args.seed, shard_id=shard, n_shards=n_shards, device=device,
                      data_prefix_len=12, max_msgs_per_window=max(1 << 20, per_window),
-                     max_records=args.max_records * (2 if acks else 1) // max(1, n_shards // 2), max_states=4096,
+                     max_records=args.max_records * (2 if acks else 1) // max(1, n_shards // 2),
+                     max_states=max(4096, rounds + 1),
                      exchange_cap=exchange_cap(per_window, n_shards))
 
 
@@ -427,7 +484,8 @@ def main():
     from testground_amd.sim import Simulator
 
     shapes = storm_shapes(args.instances, args.seed)
-    sim = Simulator(sim_config(args, rank, world, local))
+    rounds = args.warmup + probe_steps(args) + args.steps + 1
+    sim = Simulator(sim_config(args, rank, world, local, rounds))
     sim.set_stream(stream.cuda_stream)
     transport = _attach_transport(sim, dist, world, rank, rehearsal)
     sim.set_shapes(np.arange(sim.lo, sim.hi), shapes[sim.lo:sim.hi])
@@ -435,7 +493,6 @@ def main():
     N, F = args.instances, args.fanout
 
     if args.tcp:  # sharded: each rank's writers (arrivals forwarded to the writer's shard)
-        rounds = args.warmup + probe_steps(args) + args.steps + 1
         nl = sim.hi - sim.lo
         sim.tcp_enable(max_writes=rounds * nl * F, max_segments=rounds * nl * F, acks=args.tcp_acks)
 
@@ -450,16 +507,13 @@ def main():
         sim.gen_storm_round(r, T_NOW, F, args.size, spread, r)
         sim.advance_to_barrier(sim.barrier(r, N, T_NOW), rtt)
 
-    # warm-up (untimed, unprofiled), then probe steps (as many as the timed region) that time every
-    # kernel class: the dominant one is the largest total time; the timed region carries HIP events
-    # around that kernel only
+    # warm-up (untimed, unprofiled), then (--full) probe steps (as many as the timed region) that time
+    # every kernel class: the dominant one is the largest total time; the timed region carries HIP
+    # events around that kernel only. A plain run makes 10 more unprofiled steps instead.
     for r in range(args.warmup):
         step(r)
     probe = probe_steps(args)
-    warm_kernels, dominant = probe_kernels(sim, step, args.warmup, probe)
-    sim.profile([dominant] + (list(COLLECTIVES) if world > 1 else []))
-    base_all = sim.profile_read()
-    base_prof = base_all[dominant]
+    warm_kernels, dominant, base_all = settle_or_probe(args, sim, step, world > 1)
     first = args.warmup + probe
 
     s0 = counters(sim)
@@ -478,11 +532,9 @@ def main():
     s1 = counters(sim)
     tcp1 = sim.tcp_stats() if args.tcp else None
     sim_t1 = sim.now
-    prof = sim.profile_read()[dominant]
     delta = {k: s1[k] - s0[k] for k in s1}
-
-    kern_ms = prof[0] - base_prof[0]
-    kern_n = prof[1] - base_prof[1]
+    if args.dump_outputs:
+        dump_outputs(sim, args.dump_outputs, rank, world)
     delivered = delta["delivered"]
     b_total = alg_bytes_step(delta, sim.hi - sim.lo, args.steps)
     if world > 1:  # the process group is gloo: host tensors
@@ -495,14 +547,17 @@ def main():
     # (TCP lines: the PMC summaries are the message storm's, so their traffic is looked up under
     # their own workload name, which no committed summary carries: null)
     wl = ("tcp_acks" if args.tcp_acks else "tcp") if args.tcp else "storm"
-    roof = roofline(dominant, delta, kern_ms, kern_n, sim.hi - sim.lo, args.steps, wl, world, b_total, elapsed)
-    roof["kernels"] = kernel_fracs(warm_kernels, delta, sim.hi - sim.lo, args.steps, probe)
-    coll = collective_stats(sim, dist, world, base_all, args.steps, transport)
-    if coll:
-        roof["collectives"] = coll
-    cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.tcp:
-        cpu = cpu_baseline(args, shapes)
+    roof = coll = cpu = None
+    if args.full:
+        prof = sim.profile_read()[dominant]
+        kern_ms, kern_n = prof[0] - base_all[dominant][0], prof[1] - base_all[dominant][1]
+        roof = roofline(dominant, delta, kern_ms, kern_n, sim.hi - sim.lo, args.steps, wl, world, b_total, elapsed)
+        roof["kernels"] = kernel_fracs(warm_kernels, delta, sim.hi - sim.lo, args.steps, probe)
+        coll = collective_stats(sim, dist, world, base_all, args.steps, transport)
+        if coll:
+            roof["collectives"] = coll
+        if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.tcp:
+            cpu = cpu_baseline(args, shapes)
 
     if args.tcp:
         dt = {k: tcp1[k] - tcp0[k] for k in tcp1}
@@ -554,7 +609,7 @@ def main():
             "kernels_probe": warm_kernels,
         }
     sim.close()
-    if not args.no_beside:
+    if args.full and not args.no_beside:
         # config 5 at the same GPU count (the weak-scaling-friendly config beside
         # the headline, so a SCALE run carries both curves); its own defaults, no CPU baseline
         fa = argparse.Namespace(**vars(args))
@@ -725,10 +780,7 @@ def main_flood(args, ctx=None, emit=True):
     for w in range(args.warmup):
         step(w)
     probe = probe_steps(args)
-    warm_kernels, dominant = probe_kernels(sim, step, args.warmup, probe)
-    sim.profile([dominant] + (list(COLLECTIVES) if world > 1 else []))
-    base_all = sim.profile_read()
-    base_prof = base_all[dominant]
+    warm_kernels, dominant, base_all = settle_or_probe(args, sim, step, world > 1)
     first = args.warmup + probe
     s0 = counters(sim)
     sim.sync()
@@ -742,9 +794,9 @@ def main_flood(args, ctx=None, emit=True):
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     s1 = counters(sim)
-    prof = sim.profile_read()[dominant]
     delta = {k: s1[k] - s0[k] for k in s1}
-    kern_ms, kern_n = prof[0] - base_prof[0], prof[1] - base_prof[1]
+    if args.dump_outputs and emit:
+        dump_outputs(sim, args.dump_outputs, rank, world)
     delivered = delta["delivered"]
     b_total = alg_bytes_step(delta, sim.hi - sim.lo, args.steps)
     if world > 1:  # gloo process group: host tensors
@@ -753,15 +805,18 @@ def main_flood(args, ctx=None, emit=True):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dist.all_reduce(v, op=dist.ReduceOp.SUM)
         elapsed, delivered, b_total = float(t.item()), int(v[0].item()), int(v[1].item())
-    roof = roofline(dominant, delta, kern_ms, kern_n, sim.hi - sim.lo, args.steps, "flood", world, b_total,
-                    elapsed)
-    roof["kernels"] = kernel_fracs(warm_kernels, delta, sim.hi - sim.lo, args.steps, probe)
-    coll = collective_stats(sim, dist, world, base_all, args.steps, transport)
-    if coll:
-        roof["collectives"] = coll
-    cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        cpu = flood_cpu_baseline(args, shapes, graph)
+    roof = cpu = None
+    if args.full:
+        prof = sim.profile_read()[dominant]
+        kern_ms, kern_n = prof[0] - base_all[dominant][0], prof[1] - base_all[dominant][1]
+        roof = roofline(dominant, delta, kern_ms, kern_n, sim.hi - sim.lo, args.steps, "flood", world, b_total,
+                        elapsed)
+        roof["kernels"] = kernel_fracs(warm_kernels, delta, sim.hi - sim.lo, args.steps, probe)
+        coll = collective_stats(sim, dist, world, base_all, args.steps, transport)
+        if coll:
+            roof["collectives"] = coll
+        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+            cpu = flood_cpu_baseline(args, shapes, graph)
     out = None
     if rank == 0:
         out = {
@@ -849,9 +904,7 @@ def main_a2a(args):
     for r in range(args.warmup):
         step(r)
     probe = probe_steps(args)
-    warm_kernels, dominant = probe_kernels(sim, step, args.warmup, probe)
-    sim.profile([dominant])
-    base_prof = sim.profile_read()[dominant]
+    warm_kernels, dominant, base_all = settle_or_probe(args, sim, step)
     first = args.warmup + probe
     s0 = counters(sim)
     sim.sync()
@@ -863,13 +916,17 @@ def main_a2a(args):
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     s1 = counters(sim)
-    prof = sim.profile_read()[dominant]
     delta = {k: s1[k] - s0[k] for k in s1}
+    if args.dump_outputs:
+        dump_outputs(sim, args.dump_outputs)
     b_total = alg_bytes_step(delta, n, args.steps)
-    roof = roofline(dominant, delta, prof[0] - base_prof[0], prof[1] - base_prof[1], n, args.steps, "a2a", 1,
-                    b_total, elapsed)
-    roof["kernels"] = kernel_fracs(warm_kernels, delta, n, args.steps, probe)
-    cpu = None if args.no_cpu_baseline else a2a_cpu_baseline(args, n)
+    roof = cpu = None
+    if args.full:
+        prof, base_prof = sim.profile_read()[dominant], base_all[dominant]
+        roof = roofline(dominant, delta, prof[0] - base_prof[0], prof[1] - base_prof[1], n, args.steps, "a2a", 1,
+                        b_total, elapsed)
+        roof["kernels"] = kernel_fracs(warm_kernels, delta, n, args.steps, probe)
+        cpu = None if args.no_cpu_baseline else a2a_cpu_baseline(args, n)
     print(json.dumps({
         "metric": "simulated msgs delivered/sec (1k-inst all-to-all storm, config 2) + % HBM roofline",
         "value": delta["delivered"] / elapsed, "unit": "msgs/s", "n_gpus": 1, "steps": args.steps,
@@ -967,9 +1024,7 @@ def main_splitbrain(args):
     for w in range(args.warmup):
         step(w)
     probe = probe_steps(args)
-    warm_kernels, dominant = probe_kernels(sim, step, args.warmup, probe)
-    sim.profile([dominant])
-    base_prof = sim.profile_read()[dominant]
+    warm_kernels, dominant, base_all = settle_or_probe(args, sim, step)
     s0 = counters(sim)
     sim.sync()
     torch.cuda.synchronize()
@@ -980,16 +1035,21 @@ def main_splitbrain(args):
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     s1 = counters(sim)
-    prof = sim.profile_read()[dominant]
+    prof = sim.profile_read()[dominant] if args.full else None
+    if args.dump_outputs:
+        dump_outputs(sim, args.dump_outputs)
     sim.advance_begin_device(ne_ptr, 0)  # one more window and reaction, synchronised: the state after
     sim.advance_end()                    # the timed region
     ne, act = sim.probe_react()
     delta = {k: s1[k] - s0[k] for k in s1}
     b_total = alg_bytes_step(delta, n, args.steps)
-    roof = roofline(dominant, delta, prof[0] - base_prof[0], prof[1] - base_prof[1], n, args.steps, "splitbrain", 1,
-                    b_total, elapsed)
-    roof["kernels"] = kernel_fracs(warm_kernels, delta, n, args.steps, probe)
-    cpu = None if args.no_cpu_baseline else sb_cpu_baseline(args, n)
+    roof = cpu = None
+    if args.full:
+        base_prof = base_all[dominant]
+        roof = roofline(dominant, delta, prof[0] - base_prof[0], prof[1] - base_prof[1], n, args.steps, "splitbrain", 1,
+                        b_total, elapsed)
+        roof["kernels"] = kernel_fracs(warm_kernels, delta, n, args.steps, probe)
+        cpu = None if args.no_cpu_baseline else sb_cpu_baseline(args, n)
     print(json.dumps({
         "metric": "simulated msgs delivered/sec (10k-inst splitbrain, sequential probes, config 3) + % HBM roofline",
         "value": delta["delivered"] / elapsed, "unit": "msgs/s", "n_gpus": 1, "steps": args.steps,

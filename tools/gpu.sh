@@ -27,7 +27,7 @@ tests)
   rc=$?; grep -E "passed|failed|error" $OUT/tests.log | tail -3; [ $rc -eq 0 ] || tail -40 $OUT/tests.log; exit $rc;;
 bench)
   W=$1; shift
-  timeout -k 10 400 python3 -u bench.py --workload $W $(warm $W) "$@" > $OUT/bench_$W.log 2>&1 || { echo BENCH_FAIL; tail -30 $OUT/bench_$W.log; exit 1; }
+  timeout -k 10 400 python3 -u bench.py --full --workload $W $(warm $W) "$@" > $OUT/bench_$W.log 2>&1 || { echo BENCH_FAIL; tail -30 $OUT/bench_$W.log; exit 1; }
   tail -1 $OUT/bench_$W.log | cut -c1-600;;
 evidence)
   W=$1; R=$2; shift 2
@@ -36,7 +36,7 @@ evidence)
   # the profiled runs leave out the storm line's flood beside it (its windows would mix into the
   # storm's trace and counters); the bench line at the end keeps it
   NB=""; [ "$W" = storm ] && NB="--no-beside"
-  B="bench.py --workload $W --no-cpu-baseline $NB $(warm $W) $*"
+  B="bench.py --full --workload $W --no-cpu-baseline $NB $(warm $W) $*"
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/prof_$W -o run --output-format csv \
     -- python3 -u $B --steps 20 > $OUT/bench_${W}_under_rocprof.log 2>&1 || { echo PROF_FAIL; tail -20 $OUT/bench_${W}_under_rocprof.log; exit 1; }
   cp $OUT/prof_$W/run_kernel_stats.csv $P/${W}_kernel_stats.csv
@@ -50,12 +50,12 @@ evidence)
   LAST=5; [ "$W" = flood ] && LAST=8
   python3 tools/pmc_traffic.py $OUT/pmc_${W}_FETCH_SIZE/run_counter_collection.csv $OUT/pmc_${W}_WRITE_SIZE/run_counter_collection.csv \
     $P/pmc_traffic$(suffix $W).json $W 1 --last $LAST || exit 1
-  timeout -k 10 400 python3 -u bench.py --workload $W $(warm $W) "$@" > $OUT/bench_$W.log 2>&1 || { echo BENCH_FAIL; tail -30 $OUT/bench_$W.log; exit 1; }
+  timeout -k 10 400 python3 -u bench.py --full --workload $W $(warm $W) "$@" > $OUT/bench_$W.log 2>&1 || { echo BENCH_FAIL; tail -30 $OUT/bench_$W.log; exit 1; }
   tail -1 $OUT/bench_$W.log > $P/bench_$W.json
   cut -c1-600 $P/bench_$W.json;;
 pmc)
   W=$1; shift
-  B="bench.py --workload $W --no-cpu-baseline --steps 5 $(warm $W) $*"
+  B="bench.py --full --workload $W --no-cpu-baseline --steps 5 $(warm $W) $*"
   run() {
     timeout -s KILL 150 rocprofv3 --pmc $2 --kernel-include-regex "$KR" -d $OUT/$1 -o run --output-format csv \
       -- python3 -u $B > $OUT/$1.log 2>&1 || { echo "PMC_FAIL $1"; tail -5 $OUT/$1.log; exit 1; }
@@ -70,7 +70,7 @@ ab)
     for v in product "$@"; do
       if [ $v = product ]; then L=$PWD/testground_amd/libtgsim.so; else L=$PWD/testground_amd/libtgsim_$v.so; fi
       NB=""; [ "$W" = storm ] && NB="--no-beside"
-      TGSIM_LIB=$L timeout -k 10 200 python3 -u bench.py --workload $W --no-cpu-baseline $NB --steps 30 > $OUT/${W}_${v}_$r.log 2>&1 || { echo FAIL $v; tail -5 $OUT/${W}_${v}_$r.log; exit 1; }
+      TGSIM_LIB=$L timeout -k 10 200 python3 -u bench.py --full --workload $W --no-cpu-baseline $NB --steps 30 > $OUT/${W}_${v}_$r.log 2>&1 || { echo FAIL $v; tail -5 $OUT/${W}_${v}_$r.log; exit 1; }
       python3 -c "import json; j=json.loads(open('$OUT/${W}_${v}_$r.log').read().strip().splitlines()[-1]); print('$v', 'round $r', j['value'], 'msgs/s', round(j['ms_per_step'],5), 'ms/step', ' '.join('%s=%.1f' % (k, v['avg_us']) for k, v in sorted(j['kernels_probe'].items())))"
     done
   done;;
