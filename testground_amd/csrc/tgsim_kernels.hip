@@ -2280,10 +2280,13 @@ __device__ __forceinline__ bool bkt_fused_load(const BktSrc& src, const uint32_t
   {
     const uint32_t p = threadIdx.x;
     uint32_t ps, pe;
-    bkt_range_of(src, p, ps, pe);
+    // the row is read beside the sub-queue counter, not after it (one global round trip, not two):
+    // every partition block has a row allocated, and what an empty block's row holds is masked
     const uint32_t* row = poff + (size_t)p * (B + 1);
+    const uint32_t rlo = row[b], rhi = row[b + 1];
+    bkt_range_of(src, p, ps, pe);
     const bool live = ps < pe;  // an empty partition block wrote no row (bkt_local_body)
-    const uint32_t lo = live ? row[b] : 0u, hi = live ? row[b + 1] : 0u;
+    const uint32_t lo = live ? rlo : 0u, hi = live ? rhi : 0u;
     uint32_t c = hi - lo, l = lo, tc, tl;
     block_scan2(c, l, sm.part, tc, tl);  // c: items before chunk p; tc: bucket size; tl: bucket start
     cexcl[p] = c;
@@ -2405,15 +2408,17 @@ __device__ __forceinline__ bool bkt_fused_load(const BktSrc& src, const uint32_t
   }
   __syncthreads();  // cnt[k] is now the END of key k's run
   TG_PH(5);
-  // rank inside the run
+  // rank inside the run. With four workgroups per CU the LDS latency is covered by the other waves;
+  // what the phase costs is instructions issued (measured: two slots per trip with eight loads in
+  // flight was 20 % slower). So the loop over the run only counts, per comparand one
+  // compare-and-add each for "earlier" and "equal" on k1; a tie is then a slot that counted an
+  // equal entry besides itself, and only such slots walk their run again for the full-key order.
   for (uint32_t s = threadIdx.x; s < h.nb; s += kBlock) {
     const uint32_t k = sm.key[s];
     const uint32_t a = k ? sm.cnt[k - 1] : 0u, e = sm.cnt[k];
     if (e - a > kBktRankMax) continue;
-    const uint64_t x1 = sm.k1[s], x2 = sm.k2[s];
-    const uint32_t x3 = sm.k3[s];
-    // k1 alone decides almost every comparison: four k1 loads in flight, the tie-break only on ties
-    uint32_t r = 0, i = a;
+    const uint64_t x1 = sm.k1[s];
+    uint32_t r = 0, eq = 0, i = a;
     for (; i + 4 <= e; i += 4) {
       uint64_t y[4];
 #pragma unroll
@@ -2421,14 +2426,24 @@ __device__ __forceinline__ bool bkt_fused_load(const BktSrc& src, const uint32_t
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         r += y[j] < x1 ? 1u : 0u;
-        // ties only: the slot itself is skipped, or every wave would take this branch each step
-        if (y[j] == x1 && i + j != s) r += k3less(y[j], sm.k2[i + j], sm.k3[i + j], x1, x2, x3) ? 1u : 0u;
+        eq += y[j] == x1 ? 1u : 0u;
       }
     }
-    for (; i < e; ++i) {
-      const uint64_t y = sm.k1[i];
-      r += y < x1 ? 1u : 0u;
-      if (y == x1 && i != s) r += k3less(y, sm.k2[i], sm.k3[i], x1, x2, x3) ? 1u : 0u;
+    if (i < e) {  // the last one to three: one masked group (loads clamped to the run), not a loop
+      const uint32_t n = e - i;
+      const uint64_t y0 = sm.k1[i], y1 = sm.k1[n > 1 ? i + 1 : i], y2 = sm.k1[n > 2 ? i + 2 : i];
+      r += y0 < x1 ? 1u : 0u;
+      eq += y0 == x1 ? 1u : 0u;
+      r += n > 1 && y1 < x1 ? 1u : 0u;
+      eq += n > 1 && y1 == x1 ? 1u : 0u;
+      r += n > 2 && y2 < x1 ? 1u : 0u;
+      eq += n > 2 && y2 == x1 ? 1u : 0u;
+    }
+    if (eq > 1) {  // ties on k1 (the slot itself is one equal entry): the rest of the key decides
+      const uint64_t x2 = sm.k2[s];
+      const uint32_t x3 = sm.k3[s];
+      for (i = a; i < e; ++i)
+        if (i != s && sm.k1[i] == x1) r += k3less(x1, sm.k2[i], sm.k3[i], x1, x2, x3) ? 1u : 0u;
     }
     if (by_pos) sm.ord[a + r] = (uint16_t)s;
     else sm.ord[s] = (uint16_t)(a + r);
