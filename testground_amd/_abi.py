@@ -83,6 +83,18 @@ class Stats(C.Structure):
                                           "inflight", "tb_items", "extracted", "inserted", "overlimit")]
 
 
+NETSTAT_CODES = 9  # TGSIM_NETSTAT_CODES: tx_status columns, ST_QUEUED .. ST_OVERLIMIT
+# tgsim_netstat_soa (include/tgsim_netstat.h), in declaration order; every field is 8 bytes per instance
+# except tx_status (NETSTAT_CODES of them) and rx_t_last is signed
+NETSTAT_FIELDS = ("tx_msgs", "tx_bytes", "tx_queued_bytes", "tx_status", "tx_dup", "tx_clone_lost", "tx_dup_cancel",
+                  "tx_orig_overlimit", "rx_packets", "rx_bytes", "rx_corrupt", "rx_clones", "rx_reordered", "rx_local",
+                  "rx_t_last")
+
+
+class NetstatSoA(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in NETSTAT_FIELDS]
+
+
 class TcpConfig(C.Structure):
     _fields_ = [("mss", C.c_uint32), ("header_bytes", C.c_uint32), ("rto_ns", C.c_int64),
                 ("max_attempts", C.c_uint32), ("acks", C.c_uint32), ("max_writes", C.c_uint64),
@@ -228,6 +240,11 @@ _SIGS_HIP = {
     "probe_state_device": (C.c_int, [P, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "storm_state_device": (C.c_int, [P, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "kernel_counters": (C.c_int, [P, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    # include/tgsim_netstat.h
+    "netstat_enable": (C.c_int, [P, C.c_int32]),
+    "netstat_reset": (C.c_int, [P]),
+    "netstat_copy": (C.c_int, [P, C.c_uint32, C.c_size_t, C.POINTER(NetstatSoA)]),
+    "netstat_device": (C.c_int, [P, C.POINTER(NetstatSoA)]),
 }
 
 

@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "tgsim_internal.h"
+#include "../../include/tgsim_netstat.h"
 
 namespace tgsim {
 
@@ -13,7 +14,7 @@ enum KernelId : int {
   KID_SHAPE = 0, KID_EXTRACT, KID_TB, KID_EMIT, KID_RADIX_HIST, KID_RADIX_ROWS, KID_RADIX_SCATTER,
   KID_KEYS, KID_BOUNDS, KID_REGION_FILL, KID_GEN, KID_SIG, KID_LARGE, KID_BKT_HIST, KID_BKT_SCATTER,
   KID_BKT_SORT, KID_SEG_REST, KID_FLOOD_COUNT, KID_FLOOD_EMIT, KID_SHAPE_SEQ, KID_PROBE, KID_SEG_SMALL, KID_STORM,
-  KID_EXCHANGE, KID_ALLREDUCE, KID_SHAPE_WIDE, KID_COPY, KID_COUNT
+  KID_EXCHANGE, KID_ALLREDUCE, KID_SHAPE_WIDE, KID_COPY, KID_NETSTAT, KID_COUNT
 };
 extern const char* const kKernelNames[KID_COUNT];
 
@@ -362,6 +363,21 @@ struct Dev {
   unsigned long long* stats = nullptr;  // [kNSub][16] sharded k_shape counters (ST_MSGS..ST_LOCAL)
 };
 
+// Netstat (include/tgsim_netstat.h, tgsim_netstat.hip): per local instance 64-bit counters, one
+// allocation of netstat_bytes(nloc) at base (thirteen [nloc] arrays, tx_status [nloc][9], rx_t_last).
+struct NetstatDev {
+  uint64_t* base = nullptr;
+  uint64_t *tx_msgs = nullptr, *tx_bytes = nullptr, *tx_queued_bytes = nullptr, *tx_dup = nullptr,
+           *tx_clone_lost = nullptr, *tx_dup_cancel = nullptr, *tx_orig_overlimit = nullptr, *rx_packets = nullptr,
+           *rx_bytes = nullptr, *rx_corrupt = nullptr, *rx_clones = nullptr, *rx_reordered = nullptr,
+           *rx_local = nullptr, *tx_status = nullptr;
+  int64_t* rx_t_last = nullptr;
+  uint32_t nloc = 0;
+};
+inline size_t netstat_bytes(uint32_t nloc) {
+  return (size_t)(nloc ? nloc : 1u) * (13 + TGSIM_NETSTAT_CODES + 1) * 8;
+}
+
 // Times the launches issued while it is alive with a HIP event pair on d.stream (if enabled).
 struct ProfScope {
   Dev& d;
@@ -477,6 +493,13 @@ hipError_t launch_tcp_fwd(Dev& d, TcpDev& t);
 hipError_t launch_tcp_link(Dev& d, TcpDev& t, const uint32_t* links, uint32_t n);
 hipError_t launch_tcp_conn_release(Dev& d, TcpDev& t, uint32_t mode, uint32_t cur, bool base_dev,
                                    uint32_t base_host);
+// Netstat: the field pointers of an allocation; zero it (rx_t_last = INT64_MIN); the TX pass over the
+// window's staged messages (d.m_src / d.m_size as set for the window, d.status; the count as
+// window_begin takes it) and the RX pass over its sc->n_out deliveries, each one launch on d.stream.
+void netstat_bind(NetstatDev& ns, uint64_t* base, uint32_t nloc);
+hipError_t launch_netstat_reset(Dev& d, NetstatDev& ns);
+hipError_t launch_netstat_tx(Dev& d, NetstatDev& ns, uint32_t n_staged, const uint32_t* n_dev);
+hipError_t launch_netstat_rx(Dev& d, NetstatDev& ns);
 constexpr uint32_t kFloodBlocks = 4096;  // chunks of the flood reaction (>= 16 waves per CU)
 
 // Sequential probes: every local prober without a probe sends its first at t0 (device staging

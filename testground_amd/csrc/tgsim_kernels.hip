@@ -22,7 +22,8 @@ const char* const kKernelNames[KID_COUNT] = {
     "k_extract_shape", "k_extract", "k_tb_bucket", "k_emit_bucket", "k_radix_hist", "k_radix_rows", "k_radix_scatter",
     "k_keys", "k_bounds", "k_wheel_scatter", "k_gen_storm", "sync_signal", "large_segments",
     "k_bkt_hist", "k_bkt_scatter", "k_bkt_sort", "seg_rest", "k_flood_count", "k_flood_emit",
-    "k_shape_seq", "k_probe", "k_seg_small", "k_storm", "exchange", "allreduce", "k_shape_seq_wide", "k_copy_n"};
+    "k_shape_seq", "k_probe", "k_seg_small", "k_storm", "exchange", "allreduce", "k_shape_seq_wide", "k_copy_n",
+    "k_netstat"};
 
 // after a stream synchronisation: fold completed event pairs into the per-kernel totals
 static void prof_resolve(Dev& d) {

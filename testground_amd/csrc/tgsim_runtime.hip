@@ -195,6 +195,10 @@ struct tgsim_ctx {
   // (their queues end at the last chunk the reactor linked, which the host does not track)
   uint64_t storm_conn_lo = 0, storm_conn_hi = 0;
   bool storm_need_react = false;
+  // netstat (include/tgsim_netstat.h): ns.base is set once enabled (and stays: the image format of a
+  // snapshot follows it); ns_on while windows count
+  NetstatDev ns;
+  bool ns_on = false;
 };
 
 // Calls that stage messages or open a window refuse while a reaction is owed for the last one.
@@ -1341,7 +1345,10 @@ static int begin_common(tgsim_ctx* c) {
     d.m_seq = const_cast<uint32_t*>(c->ext.seq); d.m_size = const_cast<uint32_t*>(c->ext.size);
     d.m_t = const_cast<int64_t*>(c->ext.t);
   }
-  const hipError_t we = window_begin(d, c->n_staged, c->staged_dev ? &c->d.sc->n_msgs_dev : nullptr);
+  hipError_t we = window_begin(d, c->n_staged, c->staged_dev ? &c->d.sc->n_msgs_dev : nullptr);
+  // netstat's TX pass: behind the window's last status writer, on the arrays the window read
+  if (c->ns_on && we == hipSuccess)
+    we = launch_netstat_tx(d, c->ns, c->n_staged, c->staged_dev ? &c->d.sc->n_msgs_dev : nullptr);
   d.m_src = own_src; d.m_dst = own_dst; d.m_seq = own_seq; d.m_size = own_size; d.m_t = own_t;
   c->ext.n = 0;
   HIPCK(c, we, "window_begin");
@@ -1441,6 +1448,8 @@ static int tgsim_advance_end_body(tgsim_ctx* c) {
       HIPCK(c, window_end(c->d), "window_end");
     }
   }
+  // netstat's RX pass: behind the window's last delivery writer (the rest roles of the launch above)
+  if (c->ns_on) HIPCK(c, launch_netstat_rx(c->d, c->ns), "netstat");
   c->in_window = false;
   // No host round trip: a host-given end is the new clock; a device-ended window's end (and any
   // device-side error) is read at the next sync.
@@ -3473,6 +3482,9 @@ namespace {
 // changed the pend layout under version 01, so an older image was refused only by its byte total)
 constexpr uint64_t kSnapMagic = 0x3430504E53475454ull;  // "TTGSNP04": 03 + staged messages, floods, probes
 constexpr uint64_t kSnapMagicMask = 0x0000FFFFFFFFFFFFull;  // "TTGSNP" without the version
+// the image of a context that enabled netstat: the same layout + the counters as the last region
+constexpr uint64_t kSnapMagicNetstat = 0x344E504E53475454ull;  // "TTGSNPN4"
+inline uint64_t snap_magic(const tgsim_ctx* c) { return c->ns.base ? kSnapMagicNetstat : kSnapMagic; }
 
 struct SnapHeader {
   uint64_t magic, bytes;
@@ -3610,11 +3622,12 @@ void snap_regions_more(tgsim_ctx* c, std::vector<std::pair<void*, size_t>>& v) {
              {p.ans, 4 * nn}, {p.cur, 4 * nn}, {p.alist, 4 * nn}, {p.rqa, 8 * nn}})
       v.push_back(r);
   }
+  if (c->ns.base) v.push_back({c->ns.base, netstat_bytes(c->nloc)});
 }
 
 SnapHeader snap_header(tgsim_ctx* c) {
   SnapHeader h{};
-  h.magic = kSnapMagic;
+  h.magic = snap_magic(c);
   h.dev_scalars = sizeof(DevScalars);
   h.N = c->N; h.S = c->S; h.shard = c->shard; h.nloc = c->nloc; h.slots = c->d.slots;
   h.cap_rec = c->d.cap_rec; h.cap_msgs = c->d.cap_msgs; h.max_states = c->d.max_states;
@@ -3670,6 +3683,83 @@ int snap_refusal(tgsim_ctx* c) {
 
 }  // namespace
 
+// ============================== netstat (include/tgsim_netstat.h) ==============================
+// Per-instance counters of the windows' statuses and deliveries, accumulated by two launches per
+// window while enabled (tgsim_netstat.hip; hooks in begin_common and tgsim_advance_end).
+
+static int tgsim_netstat_enable_body(tgsim_ctx* c, int32_t on);
+extern "C" int tgsim_netstat_enable(tgsim_ctx* c, int32_t on) {
+  return abi_guard(c, [&] { return tgsim_netstat_enable_body(c, on); });
+}
+static int tgsim_netstat_enable_body(tgsim_ctx* c, int32_t on) {
+  if (!c) return TGSIM_EINVAL;
+  if (c->in_window) return fail(c, TGSIM_ESTATE, "netstat: inside a window");
+  if (on && !c->ns.base) {
+    alloc_point(c);
+    uint64_t* base = nullptr;
+    if (int rc = dalloc(c, &base, netstat_bytes(c->nloc) / 8)) return rc;
+    netstat_bind(c->ns, base, c->nloc);
+    HIPCK(c, launch_netstat_reset(c->d, c->ns), "netstat reset");
+  }
+  c->ns_on = on != 0;
+  return TGSIM_OK;
+}
+
+static int tgsim_netstat_reset_body(tgsim_ctx* c);
+extern "C" int tgsim_netstat_reset(tgsim_ctx* c) {
+  return abi_guard(c, [&] { return tgsim_netstat_reset_body(c); });
+}
+static int tgsim_netstat_reset_body(tgsim_ctx* c) {
+  if (!c) return TGSIM_EINVAL;
+  if (!c->ns.base) return fail(c, TGSIM_ESTATE, "netstat was never enabled");
+  if (c->in_window) return fail(c, TGSIM_ESTATE, "netstat: inside a window");
+  HIPCK(c, launch_netstat_reset(c->d, c->ns), "netstat reset");
+  return TGSIM_OK;
+}
+
+static int tgsim_netstat_copy_body(tgsim_ctx* c, uint32_t first, size_t n, const tgsim_netstat_soa* o);
+extern "C" int tgsim_netstat_copy(tgsim_ctx* c, uint32_t first, size_t n, const tgsim_netstat_soa* o) {
+  return abi_guard(c, [&] { return tgsim_netstat_copy_body(c, first, n, o); });
+}
+static int tgsim_netstat_copy_body(tgsim_ctx* c, uint32_t first, size_t n, const tgsim_netstat_soa* o) {
+  if (!c || !o) return TGSIM_EINVAL;
+  if (!c->ns.base) return fail(c, TGSIM_ESTATE, "netstat was never enabled");
+  if (first < c->lo || first > c->hi || n > (size_t)(c->hi - first))
+    return fail(c, TGSIM_EINVAL, "netstat: instances [%u, %u + %zu) outside the shard [%u, %u)", first, first, n, c->lo, c->hi);
+  int rc = sync_and_check(c);
+  if (rc) return rc;
+  if (!n) return TGSIM_OK;
+  const size_t l = first - c->lo;
+  const NetstatDev& s = c->ns;
+  const struct { void* dst; const void* src; size_t per; } f[] = {
+      {o->tx_msgs, s.tx_msgs, 1}, {o->tx_bytes, s.tx_bytes, 1}, {o->tx_queued_bytes, s.tx_queued_bytes, 1},
+      {o->tx_status, s.tx_status, TGSIM_NETSTAT_CODES}, {o->tx_dup, s.tx_dup, 1}, {o->tx_clone_lost, s.tx_clone_lost, 1},
+      {o->tx_dup_cancel, s.tx_dup_cancel, 1}, {o->tx_orig_overlimit, s.tx_orig_overlimit, 1},
+      {o->rx_packets, s.rx_packets, 1}, {o->rx_bytes, s.rx_bytes, 1}, {o->rx_corrupt, s.rx_corrupt, 1},
+      {o->rx_clones, s.rx_clones, 1}, {o->rx_reordered, s.rx_reordered, 1}, {o->rx_local, s.rx_local, 1},
+      {o->rx_t_last, s.rx_t_last, 1}};
+  for (const auto& x : f)
+    if (x.dst)
+      HIPCK(c, hipMemcpy(x.dst, static_cast<const uint64_t*>(x.src) + l * x.per, n * x.per * 8, hipMemcpyDeviceToHost), "copy");
+  return TGSIM_OK;
+}
+
+static int tgsim_netstat_device_body(tgsim_ctx* c, tgsim_netstat_soa* o);
+extern "C" int tgsim_netstat_device(tgsim_ctx* c, tgsim_netstat_soa* o) {
+  return abi_guard(c, [&] { return tgsim_netstat_device_body(c, o); });
+}
+static int tgsim_netstat_device_body(tgsim_ctx* c, tgsim_netstat_soa* o) {
+  if (!c || !o) return TGSIM_EINVAL;
+  if (!c->ns.base) return fail(c, TGSIM_ESTATE, "netstat was never enabled");
+  const NetstatDev& s = c->ns;
+  o->tx_msgs = s.tx_msgs; o->tx_bytes = s.tx_bytes; o->tx_queued_bytes = s.tx_queued_bytes; o->tx_status = s.tx_status;
+  o->tx_dup = s.tx_dup; o->tx_clone_lost = s.tx_clone_lost; o->tx_dup_cancel = s.tx_dup_cancel;
+  o->tx_orig_overlimit = s.tx_orig_overlimit; o->rx_packets = s.rx_packets; o->rx_bytes = s.rx_bytes;
+  o->rx_corrupt = s.rx_corrupt; o->rx_clones = s.rx_clones; o->rx_reordered = s.rx_reordered; o->rx_local = s.rx_local;
+  o->rx_t_last = s.rx_t_last;
+  return TGSIM_OK;
+}
+
 static int tgsim_snapshot_body(tgsim_ctx* c, void* buf, size_t cap, size_t* n);
 extern "C" int tgsim_snapshot(tgsim_ctx* c, void* buf, size_t cap, size_t* n) {
   return abi_guard(c, [&] { return tgsim_snapshot_body(c, buf, cap, n); });
@@ -3721,10 +3811,13 @@ static int tgsim_restore_body(tgsim_ctx* c, const void* buf, size_t n) {
   if (c->storm_pending) return fail(c, TGSIM_ESTATE, "restore: a storm round is pending");
   SnapReader r{static_cast<const uint8_t*>(buf), n};
   const SnapHeader h = r.val<SnapHeader>(), want = snap_header(c);
-  if (r.ok && h.magic != kSnapMagic && (h.magic & kSnapMagicMask) == (kSnapMagic & kSnapMagicMask))
+  if (r.ok && h.magic != want.magic && (h.magic == kSnapMagic || h.magic == kSnapMagicNetstat))
+    return fail(c, TGSIM_EINVAL, c->ns.base ? "restore: the image has no netstat counters, this context enabled netstat"
+                                            : "restore: the image carries netstat counters: tgsim_netstat_enable first");
+  if (r.ok && h.magic != want.magic && (h.magic & kSnapMagicMask) == (kSnapMagic & kSnapMagicMask))
     return fail(c, TGSIM_EINVAL, "restore: snapshot layout version %.2s, this library reads %.2s",
-                reinterpret_cast<const char*>(&h.magic) + 6, reinterpret_cast<const char*>(&kSnapMagic) + 6);
-  if (!r.ok || h.magic != kSnapMagic || h.bytes != n) return fail(c, TGSIM_EINVAL, "restore: not a snapshot image");
+                reinterpret_cast<const char*>(&h.magic) + 6, reinterpret_cast<const char*>(&want.magic) + 6);
+  if (!r.ok || h.magic != want.magic || h.bytes != n) return fail(c, TGSIM_EINVAL, "restore: not a snapshot image");
   SnapHeader hc = h;
   hc.bytes = 0;
   if (memcmp(&hc, &want, sizeof(SnapHeader)) != 0)

@@ -342,6 +342,33 @@ class Simulator:
         self._check(self.lib.get_stats(self._ctx, C.byref(s)))
         return {name: getattr(s, name) for name, _ in A.Stats._fields_}
 
+    # ---- per-instance traffic counters (HIP library only; tgsim_netstat.h) --------------------
+    def netstat_enable(self, on: bool = True) -> None:
+        """Count every later window's statuses (by sender) and deliveries (by receiver) on the device."""
+        self._check(self.lib.netstat_enable(self._ctx, int(bool(on))))
+
+    def netstat_reset(self) -> None:
+        self._check(self.lib.netstat_reset(self._ctx))
+
+    def netstat(self, first: int | None = None, n: int | None = None) -> dict[str, np.ndarray]:
+        """Host copies of the counters of global instances [first, first + n) (default: the whole
+        shard): uint64 [n] per field, tx_status [n, 9], rx_t_last int64 (INT64_MIN: no delivery yet)."""
+        first = self.lo if first is None else int(first)
+        n = self.hi - first if n is None else int(n)
+        out = {k: np.zeros((max(n, 0), A.NETSTAT_CODES) if k == "tx_status" else max(n, 0),
+                           np.int64 if k == "rx_t_last" else np.uint64) for k in A.NETSTAT_FIELDS}
+        if n < 0:
+            raise A.TgsimError(A.EINVAL, "netstat: negative count")
+        soa = A.NetstatSoA(**{k: _ptr(v) for k, v in out.items()})
+        self._check(self.lib.netstat_copy(self._ctx, first, n, C.byref(soa)))
+        return out
+
+    def netstat_device(self) -> dict[str, int]:
+        """Device pointers of the counter arrays, indexed by local instance (valid until close())."""
+        soa = A.NetstatSoA()
+        self._check(self.lib.netstat_device(self._ctx, C.byref(soa)))
+        return {k: int(getattr(soa, k) or 0) for k in A.NETSTAT_FIELDS}
+
     # ---- checkpoint / resume (HIP library only; tgsim.h tgsim_snapshot) ----------------------
     def snapshot(self) -> bytes:
         """The context's state at this window boundary as an opaque image (tgsim_restore)."""

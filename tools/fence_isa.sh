@@ -7,7 +7,7 @@ set -e
 cd "$(dirname "$0")/../testground_amd/csrc"
 T=$(mktemp -d)
 hipcc --version | grep -i "HIP version" || true
-for f in tgsim_kernels tgsim_probe tgsim_storm tgsim_tcp tgsim_flood tgsim_topics tgsim_runtime; do
+for f in tgsim_kernels tgsim_probe tgsim_storm tgsim_tcp tgsim_flood tgsim_topics tgsim_runtime tgsim_netstat; do
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 --offload-device-only -S -o $T/$f.s $f.hip 2>/dev/null
   n=$(grep -c buffer_wbl2 $T/$f.s || true)
   w=$(grep -A1 buffer_wbl2 $T/$f.s | grep -c 's_waitcnt vmcnt(0)' || true)

@@ -18,7 +18,8 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRCS = ["tgsim_kernels", "tgsim_probe", "tgsim_storm", "tgsim_tcp", "tgsim_flood", "tgsim_topics", "tgsim_runtime"]
+SRCS = ["tgsim_kernels", "tgsim_probe", "tgsim_storm", "tgsim_tcp", "tgsim_flood", "tgsim_topics", "tgsim_runtime",
+        "tgsim_netstat"]
 CMP = re.compile(r"^\s*v_cmpx?_\S+\s+(vcc|s\[\d+:\d+\])")
 LABEL = re.compile(r"^(\.LBB\d+_\d+|_Z\S+):")
 BACK = re.compile(r"^\s*s_cbranch_execnz\s+(\.LBB\d+_\d+)")
