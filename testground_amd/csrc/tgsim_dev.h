@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "tgsim_internal.h"
+#include "tgsim_slotdiv.h"
 #include "../../include/tgsim_netstat.h"
 
 namespace tgsim {
@@ -241,6 +242,7 @@ struct Dev {
   uint32_t data_net = 0, data_mask = 0, data_len = 0;
   uint32_t key0 = 0, key1 = 0;
   int64_t slot_ns = 1000000;
+  SlotDiv slot_div = {0, 0, 0};   // t / slot_ns by multiply-shift (slot_div_make(slot_ns) at create)
   uint32_t slots = 1024;
   uint32_t cap_msgs = 0, cap_rec = 0;
   uint32_t subcap = 0;            // per sub-queue capacity of the A/D/L batches (kNSub sub-queues)

@@ -109,15 +109,35 @@ __device__ __forceinline__ uint32_t wave_append(uint32_t* ctr) {
 // Batches A (token-bucket input), D (deliveries), L (wheel insert) are split into kNSub
 // sub-queues, each with its own counter on its own 128-B line, so that 10^5-10^6 appends per
 // window do not serialise on one address. X are the per-peer exchange blocks.
+// A pointer held in scalar registers as an opaque value. A queue base chosen per lane from kernel
+// arguments (isD ? D : L) is otherwise turned into a vector load from the kernel-argument segment
+// at a lane-varying offset, and the wait for that load (stores count in vmcnt too) drains the wave's
+// stores before every record.
+template <class T>
+__device__ __forceinline__ T* pin_scalar(T* p) {
+  // through a global-address-space pointer: behind the asm the compiler no longer sees a kernel
+  // argument, and a generic pointer would make every store through it a flat store
+  typedef __attribute__((address_space(1))) T* GlobalPtr;
+  GlobalPtr o;
+  asm volatile("s_mov_b64 %0, %1" : "=s"(o) : "s"((GlobalPtr)p));
+  return (T*)o;
+}
+// A wave-uniform 64-bit value that came through a vector load, moved to scalar registers.
+__device__ __forceinline__ int64_t uniform_i64(int64_t v) {
+  return (int64_t)(((uint64_t)__builtin_amdgcn_readfirstlane((uint32_t)((uint64_t)v >> 32)) << 32) |
+                   __builtin_amdgcn_readfirstlane((uint32_t)(uint64_t)v));
+}
+
 struct Queues {
   DevScalars* sc;
   uint32_t* qc;
   uint32_t* xq;              // exchange cursors: (peer p, slice g) at xq[(p * kXSlices + g) << 5] (qc lines 3 kNSub..)
   tgsim_record *A, *D, *L, *X;
-  uint32_t* K[3];            // group-by key of each appended record, same physical index (A, D, L)
+  uint32_t *KA, *KD, *KL;    // group-by key of each appended record, same physical index as in A / D / L
   uint32_t subcap, xcap, lo, slots;
   uint32_t xg, xcs;          // exchange slices per peer block and records per slice (x_slices / x_slice_cap)
   int64_t slot_ns;
+  SlotDiv sdiv;              // t / slot_ns without a division (tgsim_slotdiv.h; made at context creation)
   // consumer groups of A / D keys: the fused consumers give XCD x a contiguous run of buckets
   // (xcd_major), i.e. keys [gb[x-1], gb[x]); producers order each wave's A / D slots by group, so a
   // line of records is read by one XCD (whose L2 then serves its other records)
@@ -142,9 +162,7 @@ struct Queues {
   __device__ __forceinline__ uint32_t key_of(int q, const tgsim_record& r) const {
     if (q == Q_A) return r.src - lo;
     if (q == Q_D) return r.dst - lo;
-    int64_t s = r.t / slot_ns - sc->base_slot;
-    s = s < 0 ? 0 : (s > (int64_t)slots - 1 ? (int64_t)slots - 1 : s);
-    return (uint32_t)s;
+    return slot_key(sdiv, r.t, sc->base_slot, slots);
   }
   // Wave-collective: every lane of the wave calls it; salt must be wave-uniform.
   __device__ __forceinline__ void push(int q, const tgsim_record& r, uint32_t salt) const {
@@ -162,7 +180,7 @@ struct Queues {
     if (loc) {
       if (pos < subcap) {
         store_rec(buf + pos, r);
-        K[q][(size_t)(buf - (q == Q_A ? A : (q == Q_D ? D : L))) + pos] = key_of(q, r);
+        (q == Q_A ? KA : (q == Q_D ? KD : KL))[(size_t)(buf - (q == Q_A ? A : (q == Q_D ? D : L))) + pos] = key_of(q, r);
       } else {
         atomicOr(&sc->err, q == Q_A ? ERR_CAP_A : (q == Q_D ? ERR_CAP_D : ERR_CAP_L));
       }
@@ -254,7 +272,7 @@ struct Queues {
         if (pos < subcap) {
           const size_t at = (size_t)sub * subcap + pos;
           store_rec((k == Q_A ? A : (k == Q_D ? D : L)) + at, r[u]);
-          stn((k == Q_A ? K[0] : (k == Q_D ? K[1] : K[2])) + at, key_of(k, r[u]));
+          stn((k == Q_A ? KA : (k == Q_D ? KD : KL)) + at, key_of(k, r[u]));
         } else {
           atomicOr(&sc->err, k == Q_A ? ERR_CAP_A : (k == Q_D ? ERR_CAP_D : ERR_CAP_L));
         }
@@ -2558,6 +2576,11 @@ __global__ __launch_bounds__(kBlock) void k_tb_bucket(TBPolicy p, BktSrc src, co
   // line then holds records that one XCD's emit workgroups read (Queues::group_of) -, L in
   // (wave, item, lane) order from ballots.
   const Queues& Q = p.Q;
+  // the staged output's two record bases, two key bases and the window's base_slot (k_window_start
+  // wrote it; this launch comes later), in scalar registers before the loops: see pin_scalar
+  tgsim_record *const outD = pin_scalar(Q.D), *const outL = pin_scalar(Q.L);
+  uint32_t *const keyD = pin_scalar(Q.KD), *const keyL = pin_scalar(Q.KL);
+  const int64_t base_slot = uniform_i64(Q.sc->base_slot);
   uint32_t* gcnt = sm.part + 2 * (kBlock / 64);  // [8] D records per consumer group, then offsets
   uint32_t rkD[kIPT];
   uint64_t mL[kIPT];
@@ -2684,13 +2707,17 @@ __global__ __launch_bounds__(kBlock) void k_tb_bucket(TBPolicy p, BktSrc src, co
       const bool isD = q < tD;
       const uint32_t pos = isD ? sm.part[0] + q : sm.part[1] + (q - tD);
       if (pos < Q.subcap) {
+        // the key from the staged words, the two bases by value select from the pinned pointers:
+        // three stores with no load (and no wait) among them. (Q.K[isD ? ...] and isD ? Q.D : Q.L
+        // compiled to vector loads from the kernel arguments at a lane-varying offset, key_of to a
+        // load of base_slot and a 64-bit division: two full waits of the wave's stores per record)
         const size_t at = (size_t)sub * Q.subcap + pos;
-        uint4* dst = reinterpret_cast<uint4*>((isD ? Q.D : Q.L) + at);
+        const uint32_t key = isD ? a.w - Q.lo
+                                 : slot_key(Q.sdiv, (int64_t)(((uint64_t)a.y << 32) | a.x), base_slot, Q.slots);
+        uint4* dst = reinterpret_cast<uint4*>((isD ? outD : outL) + at);
         st4(dst, a.x, a.y, a.z, a.w);
         st4(dst + 1, b.x, b.y, b.z, b.w);
-        tgsim_record r;
-        r.t = (int64_t)(((uint64_t)a.y << 32) | a.x); r.src = a.z; r.dst = a.w;
-        stn(Q.K[isD ? Q_D : Q_L] + at, Q.key_of(isD ? Q_D : Q_L, r));
+        stn((isD ? keyD : keyL) + at, key);
       } else {
         atomicOr(&Q.sc->err, isD ? ERR_CAP_D : ERR_CAP_L);
       }
@@ -5288,8 +5315,7 @@ struct StormArgs {
   uint32_t F, Fp, fp_log2, size;
   uint32_t peer_m, peer_sh1, peer_sh2;  // u % (N - 1) by 32-bit multiply-shift (exact for every u32)
   int64_t spread;
-  uint64_t spread_m;         // u % spread by multiply-shift (Granlund-Montgomery, exact for every u)
-  uint32_t spread_sh1, spread_sh2;
+  SlotDiv spread_div;        // u % spread by multiply-shift (tgsim_slotdiv.h, exact for every u)
   uint32_t key0, key1, base;
   uint32_t* m_src;
   uint32_t* m_dst;
@@ -5298,12 +5324,9 @@ struct StormArgs {
   int64_t* m_t;
 };
 
-// u mod d for the launch-invariant divisor d = a.spread > 0: q = (t + ((u - t) >> sh1)) >> sh2 with
-// t = mulhi(m, u) (Granlund & Montgomery 1994, fig. 4.1; m, sh1, sh2 from storm_divisor on the host).
+// u mod d for the launch-invariant divisor d = a.spread > 0 (slot_div; its constants from the host).
 __device__ __forceinline__ uint64_t spread_mod(const StormArgs& a, uint64_t u) {
-  const uint64_t t = __umul64hi(a.spread_m, u);
-  const uint64_t q = (t + ((u - t) >> a.spread_sh1)) >> a.spread_sh2;
-  return u - q * (uint64_t)a.spread;
+  return u - slot_div(a.spread_div, u) * (uint64_t)a.spread;
 }
 
 // The peer draw out[0] % (N - 1), the same construction at 32 bits (no emulated integer division).
@@ -5497,7 +5520,7 @@ static uint32_t bkt_width_fused(const Dev& d, uint32_t K);
 static Queues make_queues(Dev& d) {
   Queues Q;
   Q.sc = d.sc; Q.qc = d.qc; Q.xq = d.qc + ((size_t)(3 * kNSub) << 5); Q.xg = x_slices(d.xcap); Q.xcs = x_slice_cap(d.xcap); Q.A = d.A; Q.D = d.D; Q.L = d.L; Q.X = d.xsend; Q.subcap = d.subcap; Q.xcap = d.xcap;
-  Q.K[0] = d.KA; Q.K[1] = d.KD; Q.K[2] = d.KL; Q.lo = d.lo; Q.slots = d.slots; Q.slot_ns = d.slot_ns;
+  Q.KA = d.KA; Q.KD = d.KD; Q.KL = d.KL; Q.lo = d.lo; Q.slots = d.slots; Q.slot_ns = d.slot_ns; Q.sdiv = d.slot_div;
   // the fused consumers' buckets (bkt_width_fused over the local keys) in xcd_major order: XCD x
   // runs buckets [x q + min(x, r), (x+1) q + min(x+1, r)) with q = B / 8, r = B % 8
   const uint32_t w = bkt_width_fused(d, d.nloc), B = (d.nloc + w - 1) / w, q8 = B >> 3, r8 = B & 7u;
@@ -5966,21 +5989,7 @@ hipError_t launch_sig_commit(Dev& d, uint32_t nparts, bool commit, uint32_t n, u
   return hipGetLastError();
 }
 
-// Multiply-shift constants of u mod d for every 64-bit u (Granlund & Montgomery 1994, fig. 4.1):
-// l = ceil(log2 d), m = floor(2^64 (2^l - d) / d) + 1, sh1 = min(l, 1), sh2 = max(l - 1, 0).
-static void storm_divisor(int64_t d, uint64_t& m, uint32_t& sh1, uint32_t& sh2) {
-  m = 0; sh1 = sh2 = 0;
-  if (d <= 0) return;
-  const uint64_t ud = (uint64_t)d;
-  uint32_t l = 0;
-  while (l < 64 && (1ull << l) < ud) ++l;
-  const unsigned __int128 two_l = (unsigned __int128)1 << l;
-  m = (uint64_t)((((unsigned __int128)1 << 64) * (two_l - ud)) / ud + 1);
-  sh1 = l < 1 ? l : 1;
-  sh2 = l > 1 ? l - 1 : 0;
-}
-
-// The same at 32 bits for the peer draw (d = N - 1 >= 1): m = floor(2^32 (2^l - d) / d) + 1 < 2^32.
+// slot_div_make at 32 bits for the peer draw (d = N - 1 >= 1): m = floor(2^32 (2^l - d) / d) + 1 < 2^32.
 static void peer_divisor(uint32_t d, uint32_t& m, uint32_t& sh1, uint32_t& sh2) {
   uint32_t l = 0;
   while (l < 32 && (1ull << l) < d) ++l;
@@ -5999,7 +6008,7 @@ static StormArgs storm_args(Dev& d, uint32_t staged_base, uint32_t round, int64_
   while (a.Fp < fanout) { a.Fp <<= 1; ++a.fp_log2; }
   peer_divisor(d.N > 1 ? d.N - 1 : 1, a.peer_m, a.peer_sh1, a.peer_sh2);
   a.size = size; a.spread = spread_ns; a.key0 = d.key0;
-  storm_divisor(spread_ns, a.spread_m, a.spread_sh1, a.spread_sh2); a.key1 = d.key1; a.base = staged_base;
+  a.spread_div = slot_div_make(spread_ns > 0 ? (uint64_t)spread_ns : 0); a.key1 = d.key1; a.base = staged_base;
   a.m_src = d.m_src; a.m_dst = d.m_dst; a.m_seq = d.m_seq; a.m_size = d.m_size; a.m_t = d.m_t;
   return a;
 }

@@ -477,6 +477,7 @@ static int create_impl(const tgsim_config* cfg, tgsim_ctx** out) {
   d.data_net = c->data_net; d.data_mask = c->data_mask; d.data_len = c->data_len;
   d.key0 = (uint32_t)cfg->seed; d.key1 = (uint32_t)(cfg->seed >> 32);
   d.slot_ns = cfg->wheel_slot_ns > 0 ? cfg->wheel_slot_ns : 1000000;
+  d.slot_div = slot_div_make((uint64_t)d.slot_ns);
   d.slots = cfg->wheel_slots ? cfg->wheel_slots : 1024;
   const uint64_t cap_msgs = cfg->max_msgs_per_window ? cfg->max_msgs_per_window : (1u << 20);
   const uint64_t cap_rec = cfg->max_records ? cfg->max_records : (1u << 22);
